@@ -100,7 +100,14 @@ def parse():
                     "ONE JSON line with the world that really ran — no GPU work (CPU-only boxes: BSX_DIST_BACKEND=gloo)")
     ap.add_argument("--collective", choices=["rccl-c", "torch"], default="rccl-c", help="N > 1: the all-gather of the data path is ncclAllGather "
                     "called by the library (bsx_pipeline_set_rccl; default) or torch.distributed through a callback")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(rank 0: the pipeline's results, a fixed sample of every witness section) as DIR/<name>.npy, float32 / float64, <= 64 MB")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.mode != "F" or args.only_leg or args.dry_run):
+        ap.error("--dump-outputs dumps the headline path: mode F, no --only-leg / --dry-run")
+    return args
 
 
 def self_launch(args):
@@ -239,6 +246,64 @@ def sharded_self_check(eng, w, J, B, V, R, rank, dev, res):
     return {"ranges": len(ks), "fields": "output64, statuses, commit result, map-job records", "witness_ranges": checked_w}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PER_CHUNK = 1 << 16          # sampled Goldilocks elements per witness / tree section per chunk
+
+
+def dump_outputs(eng, d):
+    """--dump-outputs DIR: what the caller of the timed path receives from its last step, as DIR/<name>.npy — byte arrays as
+    float32, integers as float64, every uint64 split into [low 32 bits, high 32 bits] so that each value is exact.  The results
+    (bsx_pipeline_get_results) are written whole; of every witness / Poseidon tree section a fixed sample (seeded, the same from
+    run to run) of DUMP_SAMPLE_PER_CHUNK elements per chunk, beside its [chunk, element] index.  The inputs are synth's seeded
+    workload, so two builds run with the same arguments can be compared file by file."""
+    from blobstreamx_amd import engine as E
+    eng.join()
+    res = eng.download()
+    out = {"output64": res["output64"].astype(np.float32),
+           "range_status": res["range_status"].astype(np.float64),
+           "header_status": np.array([res["header_status"]], np.float64),
+           "assemble_status": np.array([res["assemble_status"]], np.float64)}
+    for key in ("commit", "records"):              # structured records: their bytes, padding zeroed
+        if key in res:
+            a = res[key].copy()
+            a["_pad"] = 0
+            out[key + "_bytes"] = a.view(np.uint8).reshape(a.shape[0], -1).astype(np.float32)
+    if "skip_status" in res:
+        out["skip_status"] = res["skip_status"].astype(np.float64)
+    sections = []
+    if eng.with_witness:
+        sections += [("witness_map", E.BUF_WITNESS_MAP), ("witness_reduce_local", E.BUF_WITNESS_REDUCE_LOCAL),
+                     ("witness_reduce_top", E.BUF_WITNESS_REDUCE_TOP), ("witness_commit_units", E.BUF_WITNESS_COMMIT),
+                     ("witness_skip_units", E.BUF_WITNESS_SKIP)]
+    if eng.with_caps:
+        sections += [("caps_trees", E.BUF_TREES), ("caps_trees_commit_units", E.BUF_TREES_COMMIT), ("caps_trees_skip_units", E.BUF_TREES_SKIP)]
+    if eng.K > 1 and sections:
+        # with buffer sets the last step's set is the library's to know: no sample rather than one of another step
+        log(f"--dump-outputs: {eng.K} buffer sets, witness / tree sections not sampled")
+        sections = []
+    torch.cuda.synchronize(eng.dev)
+    for s, (name, which) in enumerate(sections):
+        vals, idx = [], []
+        for e in range(eng.E):
+            buf = eng.buffer(e, which, i64=True)
+            if buf.numel() == 0:
+                continue
+            rng = np.random.default_rng([0xB5A, s, e])
+            pick = np.unique(rng.integers(0, buf.numel(), min(DUMP_SAMPLE_PER_CHUNK, buf.numel()), dtype=np.int64))
+            v = buf[torch.from_numpy(pick).to(eng.dev)].cpu().numpy().view(np.uint64)
+            vals.append(np.stack([v & 0xFFFFFFFF, v >> 32], axis=1).astype(np.float64))
+            idx.append(np.stack([np.full(pick.size, e), pick], axis=1).astype(np.float64))
+        if vals:
+            out[name] = np.concatenate(vals)
+            out[name + "_index"] = np.concatenate(idx)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    log(f"--dump-outputs: {len(out)} arrays, {total / 2**20:.1f} MB -> {d}")
+
+
 # ---------------------------------------------------------------------------------------------------------------- main
 def main():
     args = parse()
@@ -261,7 +326,7 @@ def main():
         local = int(os.environ["BSX_BENCH_DEVICE"])
     pre_legs = subprocess_legs(args) if (world == 1 and args.mode == "F" and not args.no_legs) else {}
     from blobstreamx_amd import _lib
-    _lib.lib()                     # loads libbsx.so and calls bsx_prepare_process() before the first HIP call (16 hardware queues)
+    _lib.lib()                     # loads libbsx.so (after torch: one HIP runtime) before the first HIP call
     torch.cuda.set_device(local)
     dev = torch.device(f"cuda:{local}")
     backend = None
@@ -399,6 +464,8 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     headers_per_step = world * R * J * B
     value = headers_per_step / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)     # the last timed step's results, before anything steps the pipeline again
     # a second, longer loop (20 steps are 0.12 s — SURVEY §8(d)'s 100 ms with no margin): same steps, `long_run`
     long_run = None
     if args.long_steps > 0 and world == 1:

@@ -80,11 +80,6 @@ def lib():
             # libbsx.so) then binds ITS calls to the override too — loaded locally, the harness pulled in the product library beside it and
             # the A/B compared the product with itself (round 6: the lone-caller A/B was void for that reason, profiles/r6_lone_caller_ab.txt)
             L = C.CDLL(_SO, mode=C.RTLD_GLOBAL) if os.environ.get("BSX_LIB_OVERRIDE") else C.CDLL(_SO)
-            # the pipeline's 16 streams need their own hardware queues: asked for BEFORE the HIP runtime initialises (it usually has
-            # not: importing torch does not initialise HIP).  An explicit, documented call — the library itself never touches the
-            # environment (bsx.h bsx_prepare_process); BSX_KEEP_ENV=1 skips it
-            if os.environ.get("BSX_KEEP_ENV") != "1":
-                L.bsx_prepare_process()
             L.bsx_version.restype = C.c_uint32
             L.bsx_ed25519_keytable_bytes.restype = C.c_uint64
             L.bsx_ed25519_keytable_bytes_w.restype = C.c_uint64

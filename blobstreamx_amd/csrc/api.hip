@@ -64,15 +64,11 @@ hipStream_t S(bsx_ctx*, void* s) { return static_cast<hipStream_t>(s); }
 
 }  // namespace
 
-// HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue serialise.  A pipeline
-// drives 2 main + 2 commit-check streams beside the context's own two, copy and exchange streams: with 4 queues the second
-// chunk's stream lands on the first chunk's side-stream queue (measured: 3.2 -> 4.8 ms per step).  The variable is read when
-// the HIP runtime initialises, i.e. at the first HIP call of the process.  The library does NOT touch the process environment
-// (round 3's load-time constructor did): a host that wants the 16 queues calls bsx_prepare_process() before its first HIP call
-// (or exports the variable itself), and bsx_pipeline_autotune reports how many queues the pool really got.
+// HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue serialise.  The library
+// does NOT touch the process environment: the hardware-queue count is the host's choice, and bsx_pipeline_autotune picks the
+// pool streams that overlap best on whatever queues the runtime gave (and reports how many it measured).  Kept for the ABI.
 int bsx_prepare_process(void) {
-    if (getenv("GPU_MAX_HW_QUEUES")) return 0;            // the caller's choice stands
-    return setenv("GPU_MAX_HW_QUEUES", "16", 0) == 0 ? 1 : -1;
+    return 0;                                             // left alone: the caller's environment stands
 }
 
 extern "C" {
@@ -1374,6 +1370,14 @@ static int bsx_header_range_serial(bsx_ctx* ctx, uint32_t nb_map_jobs, uint32_t 
         hipStream_t s; bool active;
         ~EndCaptureOnError() { if (active) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(s, &g); if (g) (void)hipGraphDestroy(g); } }
     } cap_guard{st, capture};
+    // A capture records ONE stream and no event: the side streams' work is enqueued on `st` in program order (every wait below
+    // follows its record, so the order keeps every dependency).  The context's events are shared with the direct path, and an event
+    // recorded inside a capture stays tied to that capture — and to its graph, destroyed once instantiated — so it must not be
+    // recorded there and waited on later; a single-stream graph also has no parallel branches for the runtime to schedule (the
+    // replay ran them one after the other anyway, HISTORY.md §4).
+    if (capture) sb = s3 = s4 = st;
+    auto ev_record = [capture](hipEvent_t e, hipStream_t s) { return capture ? hipSuccess : hipEventRecord(e, s); };
+    auto ev_wait = [capture](hipStream_t s, hipEvent_t e) { return capture ? hipSuccess : hipStreamWaitEvent(s, e, 0); };
     // witness: the COMMIT unit of the target commit and the SKIP unit (include/bsx_layout.h), written by the kernels of the commit
     // chain into these compact images; expanded behind both chains
     const bsx_witness_layout CL = bsx_commit_layout(v_max), SL = bsx_skip_layout(v_max);
@@ -1391,7 +1395,7 @@ static int bsx_header_range_serial(bsx_ctx* ctx, uint32_t nb_map_jobs, uint32_t 
         HIPCHK(hipMemsetAsync(dscw.p, 0, SL.compact_stride, st));
     }
     HIPCHK(hipMemcpyAsync(io.d, io.h, io.out_off + SmallIO::OUT_BYTES, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(ctx->ev_c, st));
+    HIPCHK(ev_record(ctx->ev_c, st));
     dbuf_alias(dv, io.d + 256);
     dbuf_alias(dtv, io.d + 256 + vbytes);
     dbuf_alias(dskip, io.dout(204));
@@ -1402,24 +1406,24 @@ static int bsx_header_range_serial(bsx_ctx* ctx, uint32_t nb_map_jobs, uint32_t 
     // (the side streams' waits, the R decoding) is enqueued while the DMA runs
     const bsxk_merkle_tap tap{target_block - trusted_block, io.d + offsetof(bsx_shared_ctx, end_header_hash), dth.as<uint8_t>(), nullptr, 0, nullptr};
     RET(upload_range(ctx, st, headers, first_height, n_headers, trusted_block, range, latest_block, rd, &io, capture, &tap, /*hash_later=*/true));
-    HIPCHK(hipStreamWaitEvent(s3, ctx->ev_c, 0));                       // the commit check's inputs
+    HIPCHK(ev_wait(s3, ctx->ev_c));                       // the commit check's inputs
     RET(drd.alloc(bsxk_ed25519_rdec_bytes(v_max)));
     // s3: R decoded (a square-root chain as long as a field inversion — the longest kernel of the commit check, and it needs only the
     // validator records)
     uint8_t* tab = nullptr;
     RET(ctx_keytable(ctx, v_max, &tab, sb));
     if (tab) HIPCHK(bsxk_ed25519_decode_r(s3, dv.as<bsx_validator>(), v_max, drd.p));
-    HIPCHK(hipEventRecord(ctx->ev_d, s3));                              // the signature check waits for this
+    HIPCHK(ev_record(ctx->ev_d, s3));                              // the signature check waits for this
     // builder.skip (header_range.rs:42-48): the target header hash becomes ctx.end_header_hash (and the first output half) — stored by
     // the header hashing itself (the lane that joins the target header's tree), not by a k_fill_end_hash launch behind it
     RET(hash_range_headers(st, rd, &tap));
-    HIPCHK(hipStreamWaitEvent(sb, ctx->ev_c, 0));
-    HIPCHK(hipStreamWaitEvent(s4, ctx->ev_c, 0));
+    HIPCHK(ev_wait(sb, ctx->ev_c));
+    HIPCHK(ev_wait(s4, ctx->ev_c));
     RET(dh.alloc((size_t)v_max * 32));
     RET(dok.alloc(v_max));
     RET(dtres.alloc(sizeof(bsx_commit_result)));
     RET(dth2.alloc(32));
-    HIPCHK(hipEventRecord(ctx->ev_a, st));                              // header hashes
+    HIPCHK(ev_record(ctx->ev_a, st));                              // header hashes
     if (witness) {
         // header-field inclusion proofs of the target (chain id, height, validators_hash) and the trusted header (validators_hash)
         bsxk_field_proofs_args fa{};
@@ -1428,20 +1432,20 @@ static int bsx_header_range_serial(bsx_ctx* ctx, uint32_t nb_map_jobs, uint32_t 
         static const uint8_t hsel[BSX_SK_N_PROOFS] = {1, 1, 1, 0}, fld[BSX_SK_N_PROOFS] = {1, BSX_BLOCK_HEIGHT_INDEX, 7, 7};
         for (uint32_t k = 0; k < BSX_SK_N_PROOFS; k++)
             fa.proofs[k] = bsxk_proof_spec{hsel[k], fld[k], (uint16_t)bsx_sk_proof_cap(k), bsx_sk_off_proof(v_max, k), BSX_SK_W_LEAF_LEN + k, 0u};
-        HIPCHK(hipStreamWaitEvent(s3, ctx->ev_a, 0));                   // the range's headers are uploaded on `st`
+        HIPCHK(ev_wait(s3, ctx->ev_a));                   // the range's headers are uploaded on `st`
         HIPCHK(bsxk_field_proofs(s3, &fa));
     }
-    HIPCHK(hipEventRecord(ctx->ev_e, s3));                              // the skip conditions wait for this (field proofs)
+    HIPCHK(ev_record(ctx->ev_e, s3));                              // the skip conditions wait for this (field proofs)
     const uint8_t* d_target_hash = rd.hashes.as<uint8_t>() + (target_block - trusted_block) * 32;
     HIPCHK(bsxk_sha512_challenge(sb, dv.as<bsx_validator>(), v_max, dh.as<uint8_t>(), nullptr, v_max, cwp));
     // validator-set hash + total power of the target set: nothing here depends on the signatures — on its own stream beside the
     // challenges and the R decoding (on `sb` its 16 dependent compressions sat between the challenges and the verification: 50 us of
     // the commit chain, which had become the longer one)
     HIPCHK(bsxk_commit_tally(s4, dv.as<bsx_validator>(), 1, v_max, nullptr, nullptr, dres.as<bsx_commit_result>(), cwp));
-    HIPCHK(hipEventRecord(ctx->ev_f, s4));
+    HIPCHK(ev_record(ctx->ev_f, s4));
     // ... and the trusted set's behind it (only the skip conditions need it)
     HIPCHK(bsxk_commit_tally(s4, dtv.as<bsx_validator>(), 1, v_max, nullptr, nullptr, dtres.as<bsx_commit_result>(), swtp));
-    HIPCHK(hipEventRecord(ctx->ev_g, s4));
+    HIPCHK(ev_record(ctx->ev_g, s4));
     if (tab) {
         // the table rows are compared with the request's keys on the HOST (a mirror of the keys the rows were built for): an unchanged
         // validator set — every request of a prover's working day — launches neither the key compare nor the (no-op) build
@@ -1451,25 +1455,25 @@ static int bsx_header_range_serial(bsx_ctx* ctx, uint32_t nb_map_jobs, uint32_t 
             for (uint32_t i = 0; i < v_max; i++) memcpy(ctx->keytab_mirror.data() + 32 * (size_t)i, target_validators[i].pubkey, 32);
             ctx->keytab_mirror_valid = true;
         }
-        HIPCHK(hipStreamWaitEvent(sb, ctx->ev_d, 0));
+        HIPCHK(ev_wait(sb, ctx->ev_d));
         HIPCHK(bsxk_ed25519_verify_keyed(sb, dv.as<bsx_validator>(), dh.as<uint8_t>(), v_max, v_max, tab, v_max, ctx->btab, dok.as<uint8_t>(), nullptr, drd.p, 0));   // one commit: the table rows ARE its keys, nothing is deferred
     } else {
         HIPCHK(bsxk_ed25519_verify(sb, dv.as<bsx_validator>(), dh.as<uint8_t>(), v_max, dok.as<uint8_t>()));
-        HIPCHK(hipStreamWaitEvent(sb, ctx->ev_d, 0));
+        HIPCHK(ev_wait(sb, ctx->ev_d));
     }
-    HIPCHK(hipStreamWaitEvent(sb, ctx->ev_a, 0));                       // header hashes (target hash, field-7 checks) from `st`
-    HIPCHK(hipStreamWaitEvent(sb, ctx->ev_f, 0));                       // the target set's tally
+    HIPCHK(ev_wait(sb, ctx->ev_a));                       // header hashes (target hash, field-7 checks) from `st`
+    HIPCHK(ev_wait(sb, ctx->ev_f));                       // the target set's tally
     // the signature-dependent half of the tally (the validator leaves, the tree and the total ran EARLY, beside the R decoding)
     HIPCHK(bsxk_commit_sums(sb, dv.as<bsx_validator>(), 1, v_max, d_target_hash, dok.as<uint8_t>(), dres.as<bsx_commit_result>(), cwp));
-    HIPCHK(hipStreamWaitEvent(sb, ctx->ev_e, 0));
-    HIPCHK(hipStreamWaitEvent(sb, ctx->ev_g, 0));
+    HIPCHK(ev_wait(sb, ctx->ev_e));
+    HIPCHK(ev_wait(sb, ctx->ev_g));
     HIPCHK(bsxk_skip_check(sb, 1, v_max, rd.ranges.as<bsx_shared_ctx>(), rd.headers.as<bsx_header>(), rd.hpr, rd.hashes.as<uint8_t>(),
                            dv.as<bsx_validator>(), dtv.as<bsx_validator>(), dok.as<uint8_t>(), dres.as<bsx_commit_result>(),
                            dtres.as<bsx_commit_result>(), dskip.as<uint32_t>(), dth2.as<uint8_t>(), nullptr, chain_id, chain_id_len, swp));
-    HIPCHK(hipEventRecord(ctx->ev_b, sb));
+    HIPCHK(ev_record(ctx->ev_b, sb));
     // prove_data_commitment (header_range.rs:50-55) and the public output (:57-58); results stay in the block
     RET(run_data_commitment(ctx, st, nb_map_jobs, batch_size, rd, dth.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr, witness, nullptr, &io));
-    HIPCHK(hipStreamWaitEvent(st, ctx->ev_b, 0));
+    HIPCHK(ev_wait(st, ctx->ev_b));
     DBuf dwc, dws;
     if (witness) {
         // both chains are done: the data commitment joins the SKIP unit's public outputs (header_range.rs:58), then the two units are

@@ -184,11 +184,9 @@ typedef struct bsx_ctx bsx_ctx;
 
 /* ------------------------------------------------------------------ lifecycle */
 uint32_t bsx_version(void);
-/* OPTIONAL, once per process, BEFORE its first HIP call (the HIP runtime reads the variable when it initialises): ask for 16
- * hardware queues (GPU_MAX_HW_QUEUES=16) unless the caller's environment already sets the variable.  The pipeline tier drives up
- * to 16 streams whose kernels must overlap; on HIP's default of 4 queues they share queues (measured 3.2 -> 4.8 ms per step).
- * The library never changes the environment on its own — results do not depend on this, only the pipeline's speed.  Returns 1
- * (set), 0 (left alone: already set) or -1. */
+/* OPTIONAL, once per process, before its first HIP call.  Changes nothing: the number of hardware queues (GPU_MAX_HW_QUEUES) is
+ * the host's choice, and bsx_pipeline_autotune places the pipeline's streams on whatever queues the runtime gave.  The library
+ * never changes the environment — results do not depend on the queue count, only the pipeline's speed.  Returns 0 (left alone). */
 int bsx_prepare_process(void);
 /* device = HIP ordinal.  Fails with BSX_ERR_NO_DEVICE when no GPU is visible (no CPU fallback). */
 int bsx_init(int device, bsx_ctx** out);
@@ -410,9 +408,10 @@ int bsx_dev_free(bsx_ctx* ctx, void* ptr);
 #define BSX_TUNE_MERKLE_WORKGROUPS 1u
 /* BSX_TUNE_HOST_GRAPHS (default 0): 1 = bsx_header_range captures its launch sequence into a hipGraph the second time a shape
  *   (circuit sizes, range length, chain id) is requested and replays it from then on: one graph launch per proof request
- *   instead of ~25 kernel launches and 8 event operations.  Off by default: measured on ROCm 7.2 / MI355X the replay takes
- *   0.56 ms against 0.33 ms for the direct launches — the runtime executes the graph's three parallel branches (hashing chain,
- *   commit check, R decoding + trusted tally) one after the other, so the request pays the SUM of the chains. */
+ *   instead of ~25 kernel launches and 8 event operations.  The graph is recorded on ONE stream, with no event: the hashing
+ *   chain, commit check and R decoding + trusted tally run one after the other.  Off by default: measured on ROCm 7.2 / MI355X
+ *   the replay takes 0.56 ms against 0.33 ms for the direct launches (which overlap the chains) — the runtime had executed the
+ *   earlier three-branch graph's branches one after the other too, so the request pays the SUM of the chains. */
 #define BSX_TUNE_HOST_GRAPHS 2u
 int bsx_set_tuning(bsx_ctx* ctx, uint32_t key, uint64_t value);
 
@@ -807,9 +806,8 @@ typedef struct bsx_pipeline_autotune_result {
     uint32_t n_trials, best_trial, steps_per_trial;
     uint32_t hw_queues;                        /* how many of the pool's 16 streams can run kernels CONCURRENTLY, MEASURED (two spinning waves
                                                   on two streams take twice as long when they share a hardware queue or a dispatch pipe;
-                                                  streams are grouped greedily).  <= 4 means HIP's default GPU_MAX_HW_QUEUES: the chunks'
-                                                  streams share queues and their phases cannot overlap — call bsx_prepare_process()
-                                                  before the process's first HIP call.  11-16 on MI355X with 16 queues */
+                                                  streams are grouped greedily).  At most the GPU_MAX_HW_QUEUES the HIP runtime was
+                                                  started with (default 4) */
     double initial_ms, best_ms, worst_ms;      /* per step: the assignment the pipeline had, the one it keeps (re-timed twice as long
                                                   with the two runners-up), the slowest tried */
     uint32_t assignment[16];                   /* pool index of chunk i's main (2 i) and side (2 i + 1) stream */

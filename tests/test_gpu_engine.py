@@ -421,17 +421,17 @@ def test_pipeline_driven_from_cpp_without_python(tmp_path):
         f.write(b"".join(outs))
         f.write(np.array(rs, np.uint32).tobytes())
         f.write(np.array(ss, np.uint32).tobytes())
-    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    env = dict(os.environ)
     out = subprocess.run([os.path.join(root, "tests", "hostcheck", "pipeline_driver"), str(case)], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0 and "PIPELINE_DRIVER_OK" in out.stdout, (out.stdout[-1000:], out.stderr[-2000:])
     assert f"ranges={R} steps={steps} chunks={E}" in out.stdout
-    # bsx_prepare_process (called by the driver before its first HIP call) asked for 16 hardware queues; what the pool's streams
+    # bsx_prepare_process (called by the driver before its first HIP call) leaves the environment alone; what the pool's streams
     # really got is MEASURED by the library (groups of streams whose kernels run one after the other) and reported by
-    # bsx_pipeline_autotune: more than HIP's default of 4 (queues that share a dispatch pipe still serialise, so it
-    # need not be 16)
+    # bsx_pipeline_autotune: at least one queue, at most the GPU_MAX_HW_QUEUES the runtime started with (HIP's
+    # default 4; queues that share a dispatch pipe still serialise, so it may be fewer)
     import re
     hq = int(re.search(r"hw_queues=(\d+)", out.stdout).group(1))
-    assert 4 < hq <= 16, out.stdout
+    assert 1 <= hq <= int(env.get("GPU_MAX_HW_QUEUES", "4")), out.stdout
     # RCCL called from the C tier — a one-rank communicator made through bsx_rccl_*, ncclAllGather checked end to end
     # by bsx_pipeline_check_allgather before and after the steps; no Python, no torch in that process
     out = subprocess.run([os.path.join(root, "tests", "hostcheck", "pipeline_driver"), str(case), "--rccl"], capture_output=True, text=True, timeout=600, env=env)

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Host-side cost of enqueueing one step (ctypes + torch stream/event calls) vs the GPU time of the step."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, synth
 from blobstreamx_amd.engine import PipelinedEngines

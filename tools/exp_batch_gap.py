@@ -1,5 +1,5 @@
 import json, os, sys
-ROOT = "/root/repo" if os.path.exists("/root/repo/bench.py") else os.getcwd()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch, bench
 dev = torch.device("cuda:0")
